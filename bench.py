@@ -23,9 +23,14 @@ it: the same split of the 7B stack (`tp_llama2_7b`, `tp_llama2_7b_peer_gather`) 
 independent replicas, one token stream per GPU (`replicas`, weak scaling).  `--parallel tp` /
 `--parallel dp` make the 7B split / the replicas the `value` instead.
 
-Output: one JSON line (rank 0) with the metric, the roofline of the dominant kernel (the decode
-linear), the north-star comparison against rocBLAS/hipBLASLt fp16 GEMM, and the CPU baseline (the oracle's restatement of the reference's fake-quant QuantLinear
-forward, timed on a bounded sample on this host).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it builds
+the stack, warms up, times the K steps, writes the step's outputs when `--dump-outputs DIR` is given
+and prints one JSON line (rank 0) with the metric and the roofline of the dominant kernel as the timed
+region itself gives it.  `--full` adds everything that takes runs of its own: the other BASELINE
+configs, the decoder layers end to end, the on-box peak calibration, the north-star comparison against
+rocBLAS/hipBLASLt fp16 GEMM, the reference's kernel sweep, the prefill GEMM's own roofline, at N > 1 the
+other splits, the CPU baseline (the oracle's restatement of the reference's fake-quant QuantLinear
+forward, timed on a bounded sample on this host) and the detail file (`--detail-out`).
 """
 import argparse
 import json
@@ -118,9 +123,12 @@ def build_stack(cfg, rank, world, dev, merge=True, seed=1234, peer=False):
         for (name, N, K, abits) in launch_list(lins, merge):
             assert N % (16 * world) == 0, f"{name}: N={N} not divisible into 16-column shards for {world} ranks"
             Nl = N // world
-            wq = torch.randint(-32, 32, (Nl, K), dtype=torch.int8, device=dev, generator=g)
-            # codes have rms 18.5 and U(0.5, 1.5) has rms 1.04: unit gain per linear
-            ws = ((torch.rand((K // GROUP, Nl), device=dev, generator=g) + 0.5) / (18.5 * 1.04 * K ** 0.5)).half()
+            # symmetric codes, mean 0: with -32 among them the codes' mean of -0.5 multiplied the mean of a
+            # linear's input by 0.5 * K**0.5 / 19 ~ 1.7 per linear, the values overflowed fp16 in the sixth
+            # layer and every later linear read zeros
+            wq = torch.randint(-31, 32, (Nl, K), dtype=torch.int8, device=dev, generator=g)
+            # codes have rms 18.2 and U(0.5, 1.5) has rms 1.04: unit gain per linear
+            ws = ((torch.rand((K // GROUP, Nl), device=dev, generator=g) + 0.5) / (18.2 * 1.04 * K ** 0.5)).half()
             pk = ops.pack_w6(wq, ws)  # the weight image: 6-bit codes + blocked group scales
             del wq, ws
             if M > PREFILL_M:
@@ -219,6 +227,40 @@ def chain_runs(stack):
 def run_chains(runs):
     for r in runs:
         ops.linear_chain_w6ax(r)
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 --dump-outputs writes at most (the limit is 64 MB in all)
+
+
+def write_outputs(arrays, dirpath):
+    """--dump-outputs: `arrays` (name -> list of tensors or ndarrays, in step order) as
+    DIR/<name>.npy, float32.  Whole when everything fits DUMP_BUDGET (shape [count, ...]); otherwise
+    the same fraction of every array at fixed seeded flat positions (sorted, drawn with replacement),
+    concatenated in step order.  The same arguments give the same positions in every run and build."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(int(np.prod(t.shape)) for ts in arrays.values() for t in ts)
+    keep = min(1.0, DUMP_BUDGET / 4 / max(total, 1))
+    rng = np.random.default_rng(20240229)
+    for name, ts in arrays.items():
+        parts = []
+        for t in ts:
+            if keep < 1.0:
+                n = int(np.prod(t.shape))
+                idx = np.sort(rng.integers(0, n, max(1, int(n * keep))))
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device) if torch.is_tensor(t) else idx]
+            parts.append(t.float().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float32))
+        np.save(os.path.join(dirpath, name + ".npy"), np.stack(parts) if keep == 1.0 else np.concatenate(parts))
+
+
+def stack_outputs(stack):
+    """What a caller of the step receives: every linear's fp16 output, grouped by linear name in layer
+    order (prefill: the layers share one output buffer per linear, which holds the last layer's)."""
+    arrays = {}
+    for name, p in linears(stack):
+        outs = arrays.setdefault(name, [])
+        if all(o.data_ptr() != p["out"].data_ptr() for o in outs):
+            outs.append(p["out"])
+    return arrays
 
 
 def capture(fn, stream):
@@ -1028,12 +1070,27 @@ def main():
     ap.add_argument("--no-chain", action="store_true",
                     help="N = 1 decode: time only one launch per linear (default: also the decode chains, "
                          "fq_linear_chain_w6ax, taken for `value` when bit-identical and faster)")
-    ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="file for the full result (every comparison row); the printed line is its summary "
-                         "(<= %d chars, what the driver parses); '' = none" % LINE_MAX)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything that takes runs of its own: the other BASELINE configs, "
+                         "the decoder layers end to end, the peak calibration, the fp16 / int8 vendor comparisons, "
+                         "the reference's kernel sweep, the prefill GEMM's own roofline, at N > 1 the other splits "
+                         "and the one-GPU points, the CPU baseline, and the detail file (the --no-* switches and "
+                         "--cpu-budget select among these; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float32): every linear's output grouped by linear name, or a fixed "
+                         "seeded sample of them when they exceed %d MB; at N > 1 the step's gathered last output"
+                         % (DUMP_BUDGET >> 20))
+    ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_out", "bench_detail.json"),
+                    help="--full: file for the full result (every comparison row); the printed line is its "
+                         "summary (<= %d chars, what the driver parses); '' = none" % LINE_MAX)
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank on cuda:0, gloo with host-staged gathers, no graph")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the headline alone (set up, warm up, time the steps, print the line)
+        a.cpu_budget, a.detail_out = 0.0, ""
+        a.no_fp16_compare = a.no_calibrate = a.no_replicas = a.no_tp = a.no_c4 = True
+        a.no_extra_configs = a.no_reference_sweep = a.no_layers = True
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn_ranks(a))
@@ -1093,12 +1150,19 @@ def main():
         fused_all = r["fused_launches"]
         use_graph = r["graph"]
         finite = r["finite"]
+        if a.dump_outputs and rank == 0:
+            write_outputs({"final": [r["final"]]}, a.dump_outputs)
     else:
         stack = build_stack(cfg, rank, 1, dev, merge)
         use_graph = not a.no_graph
         replay = ctx.prepare(lambda: run_step(stack, M, 1), use_graph)
-        elapsed, ev_s = ctx.timed(replay, a.steps, a.warmup)
-        if M <= 4 and not prefill and not a.no_chain:
+        chained = M <= 4 and not prefill and not a.no_chain
+        # where the decode chains compete for the headline, a plain run times the one-launch-per-linear
+        # form over at most the default 20 + 5 steps: enough to tell which form is faster, and --steps
+        # goes to the form that is taken
+        l_steps, l_warm = (a.steps, a.warmup) if a.full or not chained else (min(a.steps, 20), min(a.warmup, 5))
+        elapsed, ev_s = ctx.timed(replay, l_steps, l_warm)
+        if chained:
             # the same step as decode chains: one persistent launch per run of linears between attention
             # cores, each linear waiting in-kernel for its input; taken for `value` only
             # when the step's output is bit-identical, no in-kernel wait timed out, and it is faster
@@ -1114,12 +1178,19 @@ def main():
                                  "each linear's weight stream issued before it waits in-kernel for its input "
                                  "(tagged hand-off granules)",
                          "launches_per_step": len(runs), "ms_per_step": round(el_c / a.steps * 1e3, 4),
-                         "launches_ms_per_step": round(elapsed / a.steps * 1e3, 4),
+                         "launches_ms_per_step": round(elapsed / l_steps * 1e3, 4),
                          "bit_identical_to_launches": same, "wait_timed_out": bool(err)}
-            if same and not err and el_c < elapsed:
+            if same and not err and el_c / a.steps < elapsed / l_steps:
                 elapsed, ev_s = el_c, ev_c
                 decode_form = f"decode chains: {len(runs)} persistent launches per step (fq_linear_chain_w6ax)"
+            elif (l_steps, l_warm) != (a.steps, a.warmup):  # the launches are the headline: --steps of them
+                elapsed, ev_s = ctx.timed(replay, a.steps, a.warmup)
+            elif a.dump_outputs:  # (the outputs written are the headline form's)
+                replay()
+                torch.cuda.synchronize()
             del replay_c
+        if a.dump_outputs and rank == 0:
+            write_outputs(stack_outputs(stack), a.dump_outputs)
         replicas = world  # independent token streams (dp), each through the whole model
         value = replicas * flops_step * a.steps / elapsed / 1e12
         tok_s = replicas * M * a.steps / elapsed
@@ -1130,9 +1201,9 @@ def main():
         fused_all = all(fused.values())
         bytes_launch = layers * sum(alg_bytes(M, N, K, ab, fused[(N, K)]) for (_, N, K, ab) in launch_lins) / n_lin
         read_launch = layers * sum(alg_read_bytes(M, N, K, ab, fused[(N, K)]) for (_, N, K, ab) in launch_lins) / n_lin
-        last = linears(stack)[-1][1]["out"]
-        finite = bool(torch.isfinite(last.float()).all().item())
-        if prefill:  # MFMA-bound: the dominant kernel is the prefill GEMM; time its launches alone
+        # every linear's output, not the last alone: a quantizer turns a non-finite input into zeros
+        finite = all(bool(torch.isfinite(o).all().item()) for outs in stack_outputs(stack).values() for o in outs)
+        if prefill and a.full:  # MFMA-bound: the dominant kernel is the prefill GEMM; time its launches alone
             codes = {}
             for name, p in linears(stack):
                 if name not in codes:
@@ -1209,7 +1280,7 @@ def main():
         res["comm"] = {"world_size": dist.get_world_size(), "backend": str(dist.get_backend()),
                        "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version())
                        if dist.get_backend() == "nccl" else None}
-    if tp > 1:  # the same workload on one GPU, same node, same run: the curve's like-for-like point
+    if tp > 1 and a.full:  # the same workload on one GPU, same node, same run: the curve's like-for-like point
         def same_1gpu():
             ms1 = measure_alone(ctx, hcfg, merge, max(2, a.steps // 2), max(1, a.warmup // 2))
             return scaling_vs_1gpu(elapsed / a.steps * 1e3, ms1, world,
@@ -1217,7 +1288,12 @@ def main():
                                    "(rank 0 alone, per-linear launches in one graph) vs its column split over the "
                                    f"{world} GPUs; vs_baseline stays null (BASELINE.md publishes no number)")
         optional(res, "same_workload_1gpu", same_1gpu, ctx)  # (rank 0 alone holds the unsharded weights)
-    if prefill and tp == 1:
+    if prefill and tp == 1 and not a.full:  # (the GEMM launches alone are timed with --full)
+        res["roofline"] = {"kernel": "fq_gemm_prefill_big_kernel" if M >= 2048 else "fq_gemm_prefill_kernel",
+                           "bound": "mfma", "achieved": None, "peak": I8_MFMA_PEAK_TOPS, "unit": "TFLOP/s",
+                           "step_ms_linears_incl_quantize": round(elapsed / a.steps * 1e3, 4),
+                           "method": "not measured: --full times the step's prefill GEMM launches alone"}
+    if prefill and tp == 1 and a.full:
         ach = ops_launch / per_gemm_s / 1e12
         bytes_pf = int(layers * sum(alg_bytes(M, N, K, ab, False) for (_, N, K, ab) in launch_lins) / n_lin)
         read_pf = int(layers * sum(alg_read_bytes(M, N, K, ab, False) for (_, N, K, ab) in launch_lins) / n_lin)

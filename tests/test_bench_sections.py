@@ -173,3 +173,33 @@ def test_round6_detail_file_folds_into_the_driver_line():
     eq = line["c3_llama2_7b_m16"]["epilogue_quantize"]
     assert eq["last_output_identical"] and "taken" not in eq  # (slower in a graph: not taken)
     assert line["roofline"]["traffic_source"].startswith("profiles/r06")
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.write_outputs (--dump-outputs): float32 .npy files, one per name; whole arrays stacked in
+    step order when they fit the budget, otherwise the same seeded positions in every call, at most the
+    budget in all."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    arrays = {"qkv": [torch.randn((3, 48), generator=g).half() for _ in range(4)],
+              "down": [torch.randn((3, 16), generator=g).half() for _ in range(4)],
+              "final": [np.arange(7, dtype=np.float16)]}
+    bench.write_outputs(arrays, str(tmp_path / "whole"))
+    for name, ts in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (len(ts),) + tuple(ts[0].shape)
+        assert np.array_equal(got, np.stack([np.asarray(t, dtype=np.float32) for t in ts]))
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 200)  # room for 200 of the 775 values
+    bench.write_outputs(arrays, str(tmp_path / "a"))
+    bench.write_outputs(arrays, str(tmp_path / "b"))
+    count = 0
+    for name, ts in arrays.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.ndim == 1 and got.size >= len(ts)
+        assert np.array_equal(got, np.load(tmp_path / "b" / f"{name}.npy"))
+        every = np.concatenate([np.asarray(t, dtype=np.float32).reshape(-1) for t in ts])
+        assert np.isin(got, every).all()
+        count += got.size
+    assert 4 * count <= 4 * 200

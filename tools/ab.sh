@@ -43,7 +43,7 @@ for rep in $(seq "$REPS"); do
                  python3 -c "$J; print(d['ms_per_step'], d['roofline']['per_launch_us'])" || exit 1 ;;
       m16)     FLEXQ_AMD_LIB=$L timeout -k 10 300 $B --no-layers --no-extra-configs --config llama2-7b-m16 2>/dev/null |
                  python3 -c "$J; print(d['ms_per_step'], d['roofline']['per_launch_us'])" || exit 1 ;;
-      e2e)     FLEXQ_AMD_LIB=$L timeout -k 10 300 $B --no-extra-configs --steps 5 --warmup 2 2>/dev/null |
+      e2e)     FLEXQ_AMD_LIB=$L timeout -k 10 300 $B --full --no-extra-configs --steps 5 --warmup 2 2>/dev/null |
                  python3 -c "$J; e=d['decoder_layers_e2e']; print(e['M1']['w6_ms_per_step'], e['M16']['w6_ms_per_step'])" || exit 1 ;;
       shapes)  echo; FQ_LIB=$L timeout -k 10 150 python3 -u tools/shape_sweep.py ${M:-1} ${SHAPES:-4096 4096 12288 4096 22016 4096 4096 11008} 2>&1 |
                  grep "us/launch" || exit 1 ;;

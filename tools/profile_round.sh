@@ -5,7 +5,7 @@ R=${1:-r01}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/prof gpurun_out/profiles
 P=gpurun_out/profiles  # merged back by gpurun; copy into profiles/ afterwards
-B="python3 bench.py --cpu-budget 0 --no-fp16-compare --no-layers --no-extra-configs --no-reference-sweep"
+B="python3 bench.py --full --cpu-budget 0 --no-fp16-compare --no-layers --no-extra-configs --no-reference-sweep"
 # 1. kernel trace + stats of the default bench (LLaMA-2-7B, M=1)
 echo "[profile_round] 1. kernel trace + stats of the default bench (LLaMA-2-7B, " ; date
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d gpurun_out/prof/kt -o run -- $B --steps 5 > gpurun_out/prof/kt.log 2>&1
@@ -23,7 +23,7 @@ p = f"gpurun_out/profiles/{sys.argv[1]}_pmc_summary.json"
 d = json.load(open(p))
 d.update(launch_pattern="qkv, o, gate_up (merged), down per layer", merged_gate_up=True,
          command="rocprofv3 --pmc FETCH_SIZE --kernel-trace --kernel-include-regex fq_gemm_decode -f csv -- "
-                 "python3 bench.py --cpu-budget 0 --no-fp16-compare --no-layers --no-extra-configs "
+                 "python3 bench.py --full --cpu-budget 0 --no-fp16-compare --no-layers --no-extra-configs "
                  "--no-reference-sweep --no-chain --steps 2 --warmup 1 --roofline-reps 1",
          note="one launch per linear (--no-chain): the chain form's linears stream the same image bytes "
               "per linear, plus 4 B per output element of hand-off granules")
@@ -53,7 +53,7 @@ p = f"gpurun_out/profiles/{sys.argv[1]}_c5_pmc_summary.json"
 d = json.load(open(p))
 d.update(merged_gate_up=True, launch_pattern="qkv, o, gate_up (merged), down per layer; the prefill GEMM launches only",
          command="rocprofv3 --pmc FETCH_SIZE --kernel-trace --kernel-include-regex fq_gemm_prefill -f csv -- "
-                 "python3 bench.py --cpu-budget 0 --no-fp16-compare --no-layers --config llama3-8b-prefill "
+                 "python3 bench.py --full --cpu-budget 0 --no-fp16-compare --no-layers --config llama3-8b-prefill "
                  "--steps 1 --warmup 1 --roofline-reps 1 --no-calibrate")
 d["source"] = f"profiles/{sys.argv[1]}_c5_pmc_fetch_size.csv"
 json.dump(d, open(p, "w"), indent=1)
